@@ -11,7 +11,13 @@ itself (the synthetic generator seeds every stream by its global index, so a ran
 the same streams of the whole batch).  Weak scaling, no collectives on the data path: the only
 collectives are the barrier around the timed region and the max-over-ranks time reduction.
 
-    python bench.py [--gpus N --steps K --warmup W] [--config 2|3|4|5] [--no-cpu]
+    python bench.py [--gpus N --steps K --warmup W] [--config 2|3|4|5] [--dump-outputs DIR] [--full [--no-cpu]]
+
+A plain run does what the headline figure needs and nothing else: it builds the batch, settles and
+warms the GPU, times the K steps and prints the line.  `--full` adds the legs reported beside the
+value (parity sample against the restatement, load-onset timing, PCIe-inclusive rates, CPU
+baseline, host front end); `--no-cpu`, `--no-e2e` and `--no-host` drop single legs of a full run.
+`--dump-outputs DIR` writes the PCM of the last timed step to DIR as .npy files (dump_outputs).
 
 `--gpus N` with N > 1 and no torch.distributed environment launches N ranks itself
 (torch.distributed.run, before this process touches the GPU) and exits with their status; under
@@ -91,9 +97,16 @@ def parse(argv=None):
                     help="jaad_stream_cfg.precision of the AAC-LC kernel: lsb1 = PCM within +-1 LSB of the "
                          "reference (BASELINE.json's bar; fused multiply-adds in the IMDCT), exact = "
                          "bit-identical; SBR/PS configs (4, 5) always decode exactly")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the host-buffer (PCIe-inclusive) leg")
-    ap.add_argument("--no-host", action="store_true", help="skip the host front-end (bitstream parse) leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs reported beside the value: parity sample against the restatement, "
+                         "load-onset (cold) timing, host-buffer (PCIe-inclusive) rates, CPU baseline, host front end")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the PCM the last timed step produced to DIR/pcm.npy (float32 "
+                         "[frame][sample][channel]) and the batch frames it holds to DIR/pcm_frames.npy (float64); a "
+                         "fixed, seeded sample of frames when the whole output would exceed the size limit")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the host-buffer (PCIe-inclusive) leg")
+    ap.add_argument("--no-host", action="store_true", help="--full: skip the host front-end (bitstream parse) leg")
     ap.add_argument("--cpu-streams", type=int, default=256, help="streams in the CPU baseline sample")
     ap.add_argument("--settle", type=float, default=0.25,
                     help="seconds of untimed back-to-back steps before the warmup: the GPU's power management "
@@ -187,6 +200,11 @@ class HipEngine:
     def pcm(self) -> np.ndarray:
         return self.pcm_dev.cpu().numpy().reshape(self.batch.n_frames, -1)
 
+    def reset(self):
+        """Every stream slot back to its fresh state (jaad_state_reset waits for the queued calls)."""
+        for slot in range(self.ctx.n_slots):
+            self.ctx.state_reset(slot)
+
     def decode_host(self) -> dict:
         """The drop-in entry (host buffers in, host PCM out): frames/s with the caller's buffers
         page-locked once (jaad_host_register, as a JNI caller pins its direct buffers) and with
@@ -215,9 +233,10 @@ class HipEngine:
         self.ctx.close()
 
 
-def run(args, engine_cls=HipEngine):
+def run(args, engine_cls=HipEngine, return_pcm=True):
     """One rank of the benchmark; returns the JSON line on rank 0 (None elsewhere) and this
-    rank's PCM after the timed steps.
+    rank's PCM after the timed steps (None without return_pcm: the command line copies it back only
+    for --dump-outputs).
 
     The ranks share nothing on the data path (north_star: "RCCL over xGMI not
     required"): the only collectives are the barrier around the timed region, the max-over-ranks
@@ -250,11 +269,11 @@ def run(args, engine_cls=HipEngine):
     dev_flags = flags | (N.HINT_SHORT_WINDOWS if short else 0)
     eng = engine_cls(cfg, batch, dev_flags, local, int(batch.stream_slot.max()) + 1 if n_frames else 1)
 
-    # ---- parity sample: the first call decodes every stream from a fresh state
+    # ---- the first call decodes every stream from a fresh state; --full: parity sample of it
     eng.step()
     eng.sync()
     parity = None
-    if rank == 0 and n_frames:
+    if args.full and rank == 0 and n_frames:
         from oracle import oracle as O
         sub = batch.select_runs(sorted({0, len(batch.stream_slot) - 1}))
         want = O.decode_batch(cfg, sub, O.Streams(int(batch.stream_slot.max()) + 1), flags, threads=2)
@@ -266,10 +285,10 @@ def run(args, engine_cls=HipEngine):
         parity = {"frames_checked": int(want.shape[0]), "max_abs_lsb": int(d.max()),
                   "samples_off_by_1": int((d == 1).sum())}
 
-    # ---- load onset: the first steps after the GPU idled (here: while the CPU checked the parity
-    # sample) run in the power manager's transient -- reported beside, never as value
+    # ---- --full, load onset: the first steps after the GPU idled (here: while the CPU checked the
+    # parity sample) run in the power manager's transient -- reported beside, never as value
     cold = None
-    if args.settle > 0 and args.steps:
+    if args.full and args.settle > 0 and args.steps:
         t1 = time.perf_counter()
         for _ in range(args.steps):
             eng.step()
@@ -283,6 +302,13 @@ def run(args, engine_cls=HipEngine):
         eng.sync()
         n_settle += 10
     t_settle = time.perf_counter() - t_settle
+    # --dump-outputs: an SBR stream's state (noise / sine table positions, smoothing ring) depends on how
+    # many calls it has decoded, and the settle phase runs for a time, not a count: the streams restart
+    # here, so that the last timed step is call (warmup - 1) + steps of fresh streams in every run.
+    # (An AAC-LC stream carries its last frame's overlap only: every call after the first gives the
+    # same PCM, and the run is left as it is.)
+    if args.dump_outputs and sbr:
+        eng.reset()
     for _ in range(max(0, args.warmup - 1)):
         eng.step()
     eng.sync()
@@ -306,15 +332,17 @@ def run(args, engine_cls=HipEngine):
         t = torch.tensor([n_frames], dtype=torch.int64)  # (a host scalar: gloo)
         dist.all_reduce(t)
         frames_all = int(t.item())
-    pcm = eng.pcm()
+    pcm = eng.pcm() if return_pcm or (args.dump_outputs and rank == 0) else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), pcm, 2048 if sbr and not N.sbr_downsampled(cfg) else 1024)
 
-    # ---- PCIe-inclusive rate (host buffers in, host PCM out), reported beside, never as value
+    # ---- --full: PCIe-inclusive rate (host buffers in, host PCM out), reported beside, never as value
     e2e = None
-    if rank == 0 and not args.no_e2e:
+    if args.full and rank == 0 and not args.no_e2e:
         e2e = eng.decode_host()
 
     cpu = None
-    if rank == 0 and not args.no_cpu:
+    if args.full and rank == 0 and not args.no_cpu:
         from oracle import oracle as O
         ns = min(args.cpu_streams if not sbr else min(args.cpu_streams, 16), len(batch.stream_slot))
         sub = batch.select_runs(range(ns))
@@ -337,7 +365,7 @@ def run(args, engine_cls=HipEngine):
                "nproc": ncores, "affinity_cpus": len(os.sched_getaffinity(0)), "cpu_model": cpu_model()}
 
     host = None
-    if rank == 0 and world == 1 and not args.no_host:
+    if args.full and rank == 0 and world == 1 and not args.no_host:
         ncores = os.cpu_count() or 1
         thr = max(1, min(ncores, len(os.sched_getaffinity(0)), int(os.environ.get("OMP_NUM_THREADS", "64") or 64)))
         host = host_front_end(args.config, thr, frames_all * args.steps / elapsed)
@@ -363,7 +391,7 @@ def run(args, engine_cls=HipEngine):
         line = {
             "metric": METRIC, "value": round(value, 1), "unit": "frames/s", "n_gpus": world, "steps": steps,
             "warmup": args.warmup, "ms_per_step": round(elapsed / steps * 1e3, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": bool(args.full),
             "config": {"workload": workload, "frames_per_gpu": n_frames, "frames_per_job": frames_all,
                        "streams_per_job": n_global_streams,
                        "parallelism": f"stream-sharded x{world} (no collectives)", "pcm": "int16 big-endian",
@@ -371,7 +399,7 @@ def run(args, engine_cls=HipEngine):
                        "lc_kernel": ("mixed-window instantiation (JAAD_HINT_SHORT_WINDOWS: the batch holds EIGHT_SHORT frames)"
                                      if short else "long-window instantiation"),
                        "precision": ("lsb1: PCM within +-1 LSB of the reference (jaad_stream_cfg.precision = "
-                                     "JAAD_PRECISION_LSB1, fused multiply-adds in the IMDCT; parity_sample checks it)"
+                                     "JAAD_PRECISION_LSB1, fused multiply-adds in the IMDCT; --full: parity_sample checks it)"
                                      if precision == N.PRECISION_LSB1 else
                                      "exact: PCM bit-identical to the reference's binary32 arithmetic")},
             "roofline": roofline(args.config, n_frames, kern_ms, achieved, traffic, traffic_src),
@@ -387,6 +415,26 @@ def run(args, engine_cls=HipEngine):
         }
     eng.close()
     return line, pcm
+
+
+DUMP_MAX_BYTES = 32 << 20  # of float32 PCM in --dump-outputs (with the frame list: well under 64 MB)
+
+
+def dump_outputs(out_dir: Path, pcm: np.ndarray, samples_per_frame: int) -> None:
+    """--dump-outputs: the PCM of the last timed step (uint8 [frame][bytes], int16 big-endian, as the
+    device entry left it) as out_dir/pcm.npy, float32 [frame][sample][channel], and the batch frames
+    those are as out_dir/pcm_frames.npy (float64).  A batch whose PCM exceeds DUMP_MAX_BYTES is
+    sampled: the same seeded choice of frames in every run of the same job."""
+    n_frames = pcm.shape[0]
+    per_frame = samples_per_frame * 2 * 4
+    keep = max(1, DUMP_MAX_BYTES // per_frame)
+    frames = np.arange(n_frames)
+    if n_frames > keep:
+        frames = np.sort(np.random.default_rng(0).choice(n_frames, keep, replace=False))
+    out = np.ascontiguousarray(pcm[frames]).view(">i2").astype(np.float32).reshape(len(frames), samples_per_frame, 2)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / "pcm.npy", out)
+    np.save(out_dir / "pcm_frames.npy", frames.astype(np.float64))
 
 
 def host_front_end(config: int, threads: int, gpu_value: float) -> dict | None:
@@ -440,7 +488,7 @@ def main(argv=None):
     if int(env_world or 1) != args.gpus:
         print(f"bench.py: WORLD_SIZE={env_world} but --gpus {args.gpus}", file=sys.stderr)
         sys.exit(2)
-    line, _ = run(args)
+    line, _ = run(args, return_pcm=False)
     if line is not None:
         print(json.dumps(line), flush=True)
     import torch.distributed as dist

@@ -1,6 +1,6 @@
 #!/bin/bash
-# Bench lines for C2 (default), C3, C4, C5 on one GPU.
-cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out; export TMPDIR=/tmp
+# Full bench lines (every leg) for C2 (default), C3, C4, C5 on one GPU -> $OUT/bench_c<config>.log
+cd "$(dirname "$0")/.." || exit 1; OUT=${OUT:-bench_out}; mkdir -p "$OUT"; export TMPDIR=/tmp
 for c in 2 3 4 5; do
-  timeout -k 10 400 python3 bench.py --config $c > gpurun_out/bench_c$c.log 2>&1 || exit $?
+  timeout -k 10 400 python3 bench.py --full --config $c > "$OUT/bench_c$c.log" 2>&1 || exit $?
 done

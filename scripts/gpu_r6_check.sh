@@ -13,4 +13,4 @@ if [ -f exp/lib_bounds.so ]; then
     --timeout-method thread > $T/bounds.log 2>&1
   rc=$?; echo "pytest rc=$rc; JAAD_BOUNDS lines: $(grep -c JAAD_BOUNDS $T/bounds.log)" >> $T/bounds.log; [ $rc -eq 0 ] || exit $rc
 fi
-timeout -k 10 400 python -u bench.py > $T/bench_c2.json 2> $T/bench_c2.err
+timeout -k 10 400 python -u bench.py --full > $T/bench_c2.json 2> $T/bench_c2.err

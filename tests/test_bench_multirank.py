@@ -12,8 +12,8 @@ import torch.multiprocessing as mp
 import bench
 from jaadec_amd import native as N
 
-SMALL = ["--config", "2", "--steps", "2", "--warmup", "2", "--settle", "0.02", "--no-cpu", "--no-e2e", "--no-host", "--streams-per-gpu", "3",
-         "--frames-per-stream", "6"]
+SMALL = ["--config", "2", "--steps", "2", "--warmup", "2", "--settle", "0.02", "--full", "--no-cpu", "--no-e2e", "--no-host",
+         "--streams-per-gpu", "3", "--frames-per-stream", "6"]
 
 
 class OracleEngine:
@@ -40,6 +40,9 @@ class OracleEngine:
 
     def pcm(self):
         return self.out.reshape(self.batch.n_frames, -1)
+
+    def reset(self):
+        self.streams = self.O.Streams(self.streams.n)
 
     def decode_host(self):
         return self.pcm()
@@ -141,6 +144,66 @@ def test_gloo_world2_bench_line_and_pcm_match_world1(monkeypatch):
     line1, pcm1 = bench.run(args, engine_cls=OracleEngine)
     assert line1["n_gpus"] == 1
     assert b"".join(got) == pcm1.tobytes()
+
+
+def _plain(config, *more):
+    return ["--config", str(config), "--steps", "3", "--warmup", "2", "--streams-per-gpu", "3", "--frames-per-stream", "6",
+            *more]
+
+
+def test_plain_run_times_the_steps_it_was_given_and_nothing_else(monkeypatch):
+    """Without --full: K timed steps, the headline fields, and none of the legs reported beside them."""
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    engines = []
+
+    class Engine(OracleEngine):
+        def __init__(self, *a):
+            super().__init__(*a)
+            engines.append(self)
+
+        def decode_host(self):
+            raise AssertionError("the host-buffer leg belongs to --full")
+
+    line, _ = bench.run(bench.parse(_plain(2, "--settle", "0.02")), engine_cls=Engine)
+    assert engines[0].n_timed == 3 and line["steps"] == 3 and line["warmup"] == 2 and line["full"] is False
+    assert line["metric"] == bench.METRIC and line["unit"] == "frames/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32" and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(3 * 6 / (line["ms_per_step"] * 1e-3), rel=1e-3)
+    for k in ("parity_sample", "cpu_baseline", "e2e_pcie_frames_per_s", "e2e_pcie_pageable_frames_per_s", "host_front_end"):
+        assert line[k] is None, k
+    assert line["settle"]["cold_ms_per_step"] is None
+
+
+@pytest.mark.parametrize("config", [2, 4])
+def test_dump_outputs_is_the_last_timed_steps_pcm_and_repeats(config, tmp_path, monkeypatch):
+    """--dump-outputs: float32 PCM of the last timed step, the same from run to run however long the
+    settle phase ran (an SBR stream's state counts its calls)."""
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    dumps = []
+    for i, settle in enumerate(("0", "0.05")):
+        d = tmp_path / f"run{i}"
+        _, pcm = bench.run(bench.parse(_plain(config, "--settle", settle, "--dump-outputs", str(d))), engine_cls=OracleEngine)
+        got, frames = np.load(d / "pcm.npy"), np.load(d / "pcm_frames.npy")
+        assert sorted(p.name for p in d.iterdir()) == ["pcm.npy", "pcm_frames.npy"]
+        assert got.dtype == np.float32 and got.shape == (18, 2048 if config == 4 else 1024, 2)
+        assert frames.dtype == np.float64 and (frames == np.arange(18)).all()
+        assert (got == pcm.view(">i2").astype(np.float32).reshape(got.shape)).all()
+        dumps.append(got)
+    assert (dumps[0] == dumps[1]).all() and np.abs(dumps[0]).max() > 0
+
+
+def test_dump_outputs_samples_a_large_output_the_same_way_every_time(tmp_path, monkeypatch):
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 5 * 1024 * 2 * 4)  # room for 5 AAC-LC frames
+    pcm = np.random.default_rng(1).integers(0, 256, (18, 1024 * 2 * 2), dtype=np.uint8)
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(d, pcm, 1024)
+    fa, fb = np.load(tmp_path / "a" / "pcm_frames.npy"), np.load(tmp_path / "b" / "pcm_frames.npy")
+    assert (fa == fb).all() and len(fa) == 5 and (np.diff(fa) > 0).all() and fa.max() < 18
+    got = np.load(tmp_path / "a" / "pcm.npy")
+    assert got.shape == (5, 1024, 2) and got.nbytes <= bench.DUMP_MAX_BYTES
+    assert (got == pcm[fa.astype(int)].view(">i2").astype(np.float32).reshape(5, 1024, 2)).all()
 
 
 def _gpu_worker(rank, world, port, q):
