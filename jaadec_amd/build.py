@@ -46,6 +46,9 @@ def _deps(*globs: str) -> list[Path]:
     return out
 
 
+# sources of libjaadgpu.so (jaadec_amd/csrc): kernels, the C-ABI host code, the bitstream front end
+GPU_SRCS = ["jaad_lc.hip", "jaad_lc_fast.hip", "jaad_sbr.hip", "jaad_ps.hip", "jaad_capi.cpp", "jaad_sbr_host.cpp",
+            "jaad_parse.cpp", "jaad_parse_sbr.cpp", "jaad_mp4.cpp"]
 # per-source extra flags (the LC kernel: see DESIGN.md §4a, scheduler strategy)
 GPU_FILE_FLAGS: dict[str, list[str]] = {
     # the +-1 LSB LC kernels (modes 4, 6): LLVM's iterative-ILP machine scheduler (-2.2 % on C2, round 6)
@@ -82,8 +85,7 @@ def build_gpu(force: bool = False, out: Path | None = None, defines: list[str] |
     the re-encoding pipeline), then linked."""
     out = out or LIB
     rewrite = VOP3_REWRITE if vop3 is None else vop3
-    srcs = [CSRC / "jaad_lc.hip", CSRC / "jaad_lc_fast.hip", CSRC / "jaad_sbr.hip", CSRC / "jaad_ps.hip", CSRC / "jaad_capi.cpp", CSRC / "jaad_sbr_host.cpp",
-            CSRC / "jaad_parse.cpp", CSRC / "jaad_parse_sbr.cpp", CSRC / "jaad_mp4.cpp"]
+    srcs = [CSRC / s for s in GPU_SRCS]
     deps = srcs + _deps("jaadec_amd/csrc/*.h", "jaadec_amd/csrc/tables/*.inc", "include/*.h") + [ROOT / "tools" / "vop3_rewrite.py"]
     if force or defines or extra or vop3 is not None or _stale(out, deps):
         objdir = ROOT / "build" / "obj" / out.stem

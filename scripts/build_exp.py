@@ -38,8 +38,8 @@ if __name__ == "__main__":
               "-fno-slp-vectorize", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function", "-I", str(ROOT / "include"), "-I", str(B.CSRC)]
     common += [f"-D{d}" for d in defs] + extra
     objs = []
-    for o in sorted(prod.glob("*.o")):
-        src = o.name[:-2]
+    for src in B.GPU_SRCS:  # (not every *.o there: an object of a source since removed may linger)
+        o = prod / (src + ".o")
         if src in srcs:
             new = objdir / o.name
             subprocess.run(common + ["-c", "-o", str(new), str(alt.get(src, B.CSRC / src))], check=True)
