@@ -1304,14 +1304,18 @@ __device__ __forceinline__ uint32_t round_pk16_lsb1(float a, float b)
 // before a younger store (it then waits for vmcnt(0)); so the prefetched loads of frame f+1 are
 // drained explicitly BEFORE frame f's PCM stores are issued.  Otherwise the first use of frame
 // f+1's inputs at the top of the loop waits for frame f's stores to reach memory.
+// What holds in the built kernels: in the +-1 LSB modes (4, 6) a long-window frame without PNS or
+// escapes has no vmcnt wait between its PCM stores and the next frame's IMDCT.  In the exact modes
+// the wave-priority exchange at the loop head is compiled to flat accesses with vmcnt(0) waits,
+// so there the wave does wait for the stores once per frame (lc_decode_kernel, loop head).
 __device__ __forceinline__ void vmem_drain() { __builtin_amdgcn_s_waitcnt(0x0F70); }  // vmcnt(0) expcnt(7) lgkmcnt(15)
 
 // PCM stores of one frame through a buffer resource covering exactly that frame: a prefix frame
 // (re-decoded only to rebuild the overlap) stores to offset >= num_records, which the hardware
-// drops.  So every frame issues the same stores: the compiler then knows that the next frame's
-// prefetched loads have exactly those stores younger than them and waits with vmcnt(N) at the
-// top of the frame loop instead of vmcnt(0) -- which would wait for the previous frame's stores
-// to reach memory (a wave would stall once per frame for the whole store round trip).
+// drops.  So every frame issues the same stores on every path, with no exec-masked branch around
+// them, and the loop head needs no VMEM wait of its own: the loads were drained before the stores
+// (vmem_drain), and nothing at the top of the frame loop has to wait for the previous frame's
+// stores to reach memory (which holds in the +-1 LSB modes only: see vmem_drain).
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t frame_rsrc(void* base, int bytes)
 {
     return __builtin_amdgcn_make_buffer_rsrc(base, (short)0, bytes, 0x00020000);  // gfx9 raw buffer
@@ -1747,29 +1751,41 @@ __global__ __launch_bounds__(64 * waves_per_wg<kMode == 1 || kMode == 3>()) void
             // SIMDs in a fixed cyclic order); the one with the most frames left gets the highest
             // priority, so that they end together (C2 wave ends 132-171 -> 147-160 us, busy 88 ->
             // 95 % of span x waves; batch -1 %, profiles/round5_balance/).
-#if defined(JAAD_PRIO_LATE)  // (A/B builds: the mates' counts read here, the priority set after the IQ)
-            const uint32_t rem_late = (uint32_t)(my_n - it);
-            uint32_t mates_late[kW / 4 - 1];
-            {
-                volatile uint32_t* R = S.rem;
-                R[wave] = rem_late;
-#pragma unroll
-                for (int m = 1; m < kW / 4; m++) mates_late[m - 1] = R[(wave + 4 * m) % kW];
-            }
-#elif !defined(JAAD_ABL_NOPRIO)
+            // The +-1 LSB modes exchange the counts with relaxed workgroup-scope atomics, which
+            // compile to ds_write_b32 / ds_read_b32 under lgkmcnt.  The volatile accesses of the
+            // exact modes go through the flat path, whose vmcnt(0) waits make the wave wait here
+            // for the previous frame's PCM stores ("LSB1 loop head").
+#if !defined(JAAD_ABL_NOPRIO)
 #ifndef JAAD_PRIO_EVERY  // (A/B builds: the priority recomputed every N frames)
 #define JAAD_PRIO_EVERY 1
 #endif
             if ((it % JAAD_PRIO_EVERY) == 0) {
                 const uint32_t rem = (uint32_t)(my_n - it);
-                volatile uint32_t* R = S.rem;
-                R[wave] = rem;
                 int p = 0;
+                if constexpr (kFast) {
+                    __hip_atomic_store(&S.rem[wave], rem, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    uint32_t mates[kW / 4 - 1];
 #pragma unroll
-                for (int m = 1; m < kW / 4; m++) {
-                    const int mate = (wave + 4 * m) % kW;
-                    const uint32_t r = __builtin_amdgcn_readfirstlane(R[mate]);
-                    p += (rem > r || (rem == r && wave > mate)) ? 1 : 0;
+                    for (int m = 1; m < kW / 4; m++)
+                        mates[m - 1] = __hip_atomic_load(&S.rem[(wave + 4 * m) % kW], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    // (count, wave) compared as one key: the same order as the exact modes' test
+                    // below, without a per-mate tie-break mask held in SGPRs across the frame
+                    static_assert(kW <= 16, "the key keeps the wave in 4 bits");
+                    const uint32_t key = (rem << 4) | (uint32_t)wave;
+#pragma unroll
+                    for (int m = 1; m < kW / 4; m++) {
+                        const uint32_t mate = (uint32_t)((wave + 4 * m) % kW);
+                        p += key > ((__builtin_amdgcn_readfirstlane(mates[m - 1]) << 4) | mate) ? 1 : 0;
+                    }
+                } else {
+                    volatile uint32_t* R = S.rem;
+                    R[wave] = rem;
+#pragma unroll
+                    for (int m = 1; m < kW / 4; m++) {
+                        const int mate = (wave + 4 * m) % kW;
+                        const uint32_t r = __builtin_amdgcn_readfirstlane(R[mate]);
+                        p += (rem > r || (rem == r && wave > mate)) ? 1 : 0;
+                    }
                 }
                 if (p >= 2) __builtin_amdgcn_s_setprio(3);
                 else if (p == 1) __builtin_amdgcn_s_setprio(2);
@@ -1911,20 +1927,6 @@ __global__ __launch_bounds__(64 * waves_per_wg<kMode == 1 || kMode == 3>()) void
                 STAMP(13);
                 if (stereo) iq_channel(T, A.iq_table, cur.q[1], gR, xR);
             }
-#if defined(JAAD_PRIO_LATE)
-            {
-                int p = 0;
-#pragma unroll
-                for (int m = 1; m < kW / 4; m++) {
-                    const int mate = (wave + 4 * m) % kW;
-                    const uint32_t r = __builtin_amdgcn_readfirstlane(mates_late[m - 1]);
-                    p += (rem_late > r || (rem_late == r && wave > mate)) ? 1 : 0;
-                }
-                if (p >= 2) __builtin_amdgcn_s_setprio(3);
-                else if (p == 1) __builtin_amdgcn_s_setprio(2);
-                else __builtin_amdgcn_s_setprio(1);
-            }
-#endif
             // the inputs are consumed: frame f+1's loads fly while this frame's IMDCTs run
             STAMP(12);
             // issued on every iteration (the last one reloads its own frame) so that the VMEM
@@ -2147,7 +2149,9 @@ __global__ __launch_bounds__(64 * waves_per_wg<kMode == 1 || kMode == 3>()) void
             STAMP(10);
         }
         STAMP(11);
-        reinterpret_cast<volatile uint32_t*>(S.rem)[wave] = 0u;  // (done: no longer ahead of its mates)
+        // (done: no longer ahead of its mates)
+        if constexpr (kFast) __hip_atomic_store(&S.rem[wave], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        else reinterpret_cast<volatile uint32_t*>(S.rem)[wave] = 0u;
         if (cd.info & kChunkStoreState) {
             const int u = lane_id();
             float* st = A.state_out + (size_t)cd.slot * 2048;
