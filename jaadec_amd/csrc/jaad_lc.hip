@@ -1419,10 +1419,26 @@ struct Prefetch {
     uint32_t sf2[2], cb2[2];  // [channel] sf / cb bytes of bands 2u, 2u+1 (zero-extended 16 bits)
     uint32_t side;     // lane i < 4*nch: dword i of the frame's jaad_ics_info records;
                        // lanes 8..11: the frame's ms_used words (read back with readlane)
+                       // (+-1 LSB modes: see kSideByRow)
 };
+// Side-word layout of the +-1 LSB modes (prefetch<true>): the upper half of each 16-lane row r
+// (lanes 16 r + 8 .. 16 r + 15) holds ms_used word r, which is the word with the M/S bits of that
+// row's bands 2u, 2u+1; one row rotation hands it to the row's lower half, and no word goes through
+// SGPRs.  The skip entry is then in lanes 17 / 16, not 63 / 62.
+#if defined(JAAD_MS_READLANE)  // (A/B builds: the exact modes' layout in every mode)
+constexpr bool kSideByRow = false;
+#else
+constexpr bool kSideByRow = true;
+#endif
+template <bool F>
+constexpr int skip_lane()  // lane of the skip entry's first frame; the run's length is in the lane below
+{
+    return F && kSideByRow ? 17 : 63;
+}
 
 // Everything frame f needs from HBM, as vector loads (vmcnt is in order; scalar loads would
 // share lgkmcnt with the LDS traffic and could not be left in flight).
+template <bool F>
 __device__ __forceinline__ void prefetch(const KernelArgs& A, int f, bool stereo, int u, Prefetch& pf, int skip = 0)
 {
     const int nch = stereo ? 2 : 1;
@@ -1436,6 +1452,15 @@ __device__ __forceinline__ void prefetch(const KernelArgs& A, int f, bool stereo
         // lane u's two bands straight from the rows (no LDS round trip to regroup row dwords)
         pf.sf2[c] = reinterpret_cast<const uint16_t*>(A.sf + cf * 128)[u];
         pf.cb2[c] = reinterpret_cast<const uint16_t*>(A.cb + cf * 128)[u];
+    }
+    if constexpr (F && kSideByRow) {  // (a lane that no one reads loads some valid word)
+        const uint32_t* side = u < 8 ? reinterpret_cast<const uint32_t*>(A.ics + (size_t)f * A.cf_stride) + (u < 4 * nch ? u : 0)
+                                     : (A.ms_used ? reinterpret_cast<const uint32_t*>(A.ms_used + (size_t)f * 2 * A.ms_stride) + (u >> 4)
+                                                  : reinterpret_cast<const uint32_t*>(A.ics));
+        constexpr int ks = skip_lane<F>();  // the skip entry as below, in lanes ks / ks - 1
+        if (A.skips && (u | 1) == ks) side = A.skips + 2 * skip + (u == ks - 1);
+        pf.side = *side;
+        return;
     }
     const uint32_t* side = u < 8 ? reinterpret_cast<const uint32_t*>(A.ics + (size_t)f * A.cf_stride) + (u < 4 * nch ? u : 0)
                                  : (A.ms_used ? reinterpret_cast<const uint32_t*>(A.ms_used + (size_t)f * 2 * A.ms_stride) + (u & 3)
@@ -1621,6 +1646,7 @@ __device__ __forceinline__ void synth_channel(const KernelArgs& A, const LdsTabl
 // it is issued; a failing check prints the chunk, the frame, what was accessed and the two values
 // compared, and the wave leaves the kernel (the conditions are wave-uniform).  Product builds
 // compile the checks away (the chunk-level guard below stays).
+#define JAAD_BOUND_RETURN return  // (return false inside lc_decode_kernel's frame lambda)
 #ifdef JAAD_BOUNDS
 #define JAAD_BOUND(ci, f, cond, what, a, b)                                                                 \
     do {                                                                                                   \
@@ -1628,7 +1654,7 @@ __device__ __forceinline__ void synth_channel(const KernelArgs& A, const LdsTabl
             if (lane_id() == 0)                                                                            \
                 printf("JAAD_BOUNDS lc_decode_kernel: chunk %u frame %d: %s %u vs %u\n", (unsigned)(ci), (int)(f), \
                        what, (unsigned)(a), (unsigned)(b));                                                \
-            return;                                                                                        \
+            JAAD_BOUND_RETURN;                                                                             \
         }                                                                                                  \
     } while (0)
 #else
@@ -1741,10 +1767,21 @@ __global__ __launch_bounds__(64 * waves_per_wg<kMode == 1 || kMode == 3>()) void
         int skip = (int)cd.skip;
         int fr_next = f_first;  // batch frame of the iteration's frame
         Prefetch pf;
-        if (my_n > 0) prefetch(A, fr_next, stereo, lane_id(), pf, skip);
+        if (my_n > 0) prefetch<kFast>(A, fr_next, stereo, lane_id(), pf, skip);
         vmem_drain();  // (see vmem_drain) the loop head then finds no load pending on any path
 
+        // One frame of the chunk (iteration `it`).  In the +-1 LSB modes' translation unit the body
+        // is a lambda, so that the frame loop can run unrolled by two, below (always inlined; false
+        // only from a JAAD_BOUNDS check).  The exact modes keep the plain loop: behind the lambda
+        // their device code would not stay what it is.
+#if defined(JAAD_LC_FAST_TU) && !defined(JAAD_NO_UNROLL2)  // (JAAD_NO_UNROLL2: A/B builds)
+#define JAAD_FRAME_LAMBDA
+#undef JAAD_BOUND_RETURN
+#define JAAD_BOUND_RETURN return false
+        const auto frame = [&](const int it) __attribute__((always_inline)) -> bool {
+#else
         for (int it = 0; it < my_n; it++) {
+#endif
             // Issue arbitration between the waves of a SIMD favours the oldest wave: left alone,
             // the three waves of a SIMD end ~12 us apart and the last ones run with their latency
             // exposed.  The waves sharing this wave's SIMD are w +- 4 (a workgroup's waves go to the
@@ -1775,7 +1812,14 @@ __global__ __launch_bounds__(64 * waves_per_wg<kMode == 1 || kMode == 3>()) void
 #pragma unroll
                     for (int m = 1; m < kW / 4; m++) {
                         const uint32_t mate = (uint32_t)((wave + 4 * m) % kW);
-                        p += key > ((__builtin_amdgcn_readfirstlane(mates[m - 1]) << 4) | mate) ? 1 : 0;
+                        const uint32_t mkey = (__builtin_amdgcn_readfirstlane(mates[m - 1]) << 4) | mate;
+#if defined(JAAD_PRIO_VALU)  // (A/B builds: the count as the compiler forms it, through v_cndmask)
+                        p += key > mkey ? 1 : 0;
+#else
+                        // counted on the scalar unit: compare, then SCC selected (first mate) or added
+                        if (m == 1) asm("s_cmp_gt_u32 %1, %2\n\ts_cselect_b32 %0, 1, 0" : "=s"(p) : "s"(key), "s"(mkey) : "scc");
+                        else asm("s_cmp_gt_u32 %1, %2\n\ts_addc_u32 %0, %0, 0" : "+s"(p) : "s"(key), "s"(mkey) : "scc");
+#endif
                     }
                 } else {
                     volatile uint32_t* R = S.rem;
@@ -1787,6 +1831,13 @@ __global__ __launch_bounds__(64 * waves_per_wg<kMode == 1 || kMode == 3>()) void
                         p += (rem > r || (rem == r && wave > mate)) ? 1 : 0;
                     }
                 }
+#if !defined(JAAD_PRIO_VALU)
+                if constexpr (kFast) {  // one rising chain: no else branches to structure
+                    __builtin_amdgcn_s_setprio(1);
+                    if (p >= 1) __builtin_amdgcn_s_setprio(2);
+                    if (p >= 2) __builtin_amdgcn_s_setprio(3);
+                } else
+#endif
                 if (p >= 2) __builtin_amdgcn_s_setprio(3);
                 else if (p == 1) __builtin_amdgcn_s_setprio(2);
                 else __builtin_amdgcn_s_setprio(1);
@@ -1802,8 +1853,8 @@ __global__ __launch_bounds__(64 * waves_per_wg<kMode == 1 || kMode == 3>()) void
             const size_t cf0 = (size_t)f * A.cf_stride;
             const Prefetch cur = pf;
             fr_next = f + 1;
-            if (A.skips && fr_next == __builtin_amdgcn_readlane(cur.side, 63)) {  // step over dropped frames
-                fr_next += __builtin_amdgcn_readlane(cur.side, 62);
+            if (A.skips && fr_next == __builtin_amdgcn_readlane(cur.side, skip_lane<kFast>())) {  // step over dropped frames
+                fr_next += __builtin_amdgcn_readlane(cur.side, skip_lane<kFast>() - 1);
                 skip++;
             }
             // (JAAD_BOUNDS: the frame this iteration decodes was prefetched in the previous one; the
@@ -1834,8 +1885,10 @@ __global__ __launch_bounds__(64 * waves_per_wg<kMode == 1 || kMode == 3>()) void
             const bool ms_on = stereo && (iL.flags & JAAD_ICS_COMMON_WINDOW) && (iL.flags & JAAD_ICS_MS_PRESENT);
             const bool is_on = stereo && (iR.flags & JAAD_ICS_HAS_IS);
             const bool same_bands = !stereo || (iL.seq == iR.seq && iL.max_sfb == iR.max_sfb && iL.grouping == iR.grouping);
+            constexpr bool kMsByRow = kFast && kSideByRow;
+            const bool ms_bits = ms_on && A.ms_used;  // (else every ms_used bit counts as 0)
             uint64_t m0 = 0, m1 = 0;
-            if (ms_on && A.ms_used) {
+            if (!kMsByRow && ms_bits) {
                 // readlane returns int: widen through uint32_t (no sign extension)
                 m0 = (uint64_t)(uint32_t)__builtin_amdgcn_readlane(cur.side, 8) |
                      ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(cur.side, 9) << 32);
@@ -1848,8 +1901,15 @@ __global__ __launch_bounds__(64 * waves_per_wg<kMode == 1 || kMode == 3>()) void
             {
                 const uint32_t sfL2 = cur.sf2[0], cbL2 = cur.cb2[0];
                 const uint32_t sfR2 = stereo ? cur.sf2[1] : 0u, cbR2 = stereo ? cur.cb2[1] : 0u;
-                const uint64_t mw = u < 32 ? m0 : m1;
-                const uint32_t msb = (uint32_t)(mw >> ((2 * u) & 63)) & 3u;
+                uint32_t msb;
+                if constexpr (kMsByRow) {
+                    // row_ror:8 into banks 0-1 of every row: lanes 16r .. 16r+7 take lanes 16r+8 .. 16r+15
+                    const uint32_t mw = (uint32_t)__builtin_amdgcn_update_dpp((int)cur.side, (int)cur.side, 0x128, 0xf, 0x3, false);
+                    msb = (mw >> ((2 * u) & 31)) & 3u;
+                } else {
+                    const uint64_t mw = u < 32 ? m0 : m1;
+                    msb = (uint32_t)(mw >> ((2 * u) & 63)) & 3u;
+                }
                 BandRec br[2];
 #pragma unroll
                 for (int e = 0; e < 2; e++) {
@@ -1862,14 +1922,14 @@ __global__ __launch_bounds__(64 * waves_per_wg<kMode == 1 || kMode == 3>()) void
                     // non-spectral bands get -0.0: q is 0 there and iq_signed[0] = -0.0, so the
                     // product is the reference's +0.0 (ICStream.java:236-239) without a select
                     br[e].gl = (inL && cbL != JAAD_ZERO_HCB && cbL < JAAD_NOISE_HCB) ? gvL : kZeroBandGain;
-                    br[e].ms = (ms_on && inL && msbit && cbL < JAAD_NOISE_HCB && cbR < JAAD_NOISE_HCB) ? 1.0f : 0.0f;
+                    br[e].ms = ((kMsByRow ? ms_bits : ms_on) && inL && msbit && cbL < JAAD_NOISE_HCB && cbR < JAAD_NOISE_HCB) ? 1.0f : 0.0f;
                     float gr = 0.0f, is = 0.0f;
                     if (stereo) {
                         const float gvR = T.sf_gain[sfR];
                         gr = (inR && cbR != JAAD_ZERO_HCB && cbR < JAAD_NOISE_HCB) ? gvR : kZeroBandGain;
                         if (is_on && inR && (cbR == JAAD_INTENSITY_HCB || cbR == JAAD_INTENSITY_HCB2)) {
                             float cs = cbR == JAAD_INTENSITY_HCB ? 1.0f : -1.0f;
-                            if ((iL.flags & JAAD_ICS_MS_PRESENT) && msbit) cs = -cs;
+                            if ((kMsByRow ? ms_bits : (iL.flags & JAAD_ICS_MS_PRESENT) != 0) && msbit) cs = -cs;
                             is = cs * gvR;
                         }
                     }
@@ -1934,7 +1994,7 @@ __global__ __launch_bounds__(64 * waves_per_wg<kMode == 1 || kMode == 3>()) void
 #ifdef JAAD_ABL_NOPREF
             if (it == 0)
 #endif
-            prefetch(A, it + 1 < my_n ? fr_next : f, stereo, u, pf, skip);
+            prefetch<kFast>(A, it + 1 < my_n ? fr_next : f, stereo, u, pf, skip);
 
             if ((iL.flags | (stereo ? iR.flags : 0)) & JAAD_ICS_HAS_PNS) {  // rare: lane 0 replays the LCG
                 // pns_fill reads the channel's raw sf/cb rows from rsp
@@ -2147,7 +2207,25 @@ __global__ __launch_bounds__(64 * waves_per_wg<kMode == 1 || kMode == 3>()) void
                 }
             }
             STAMP(10);
+#ifdef JAAD_FRAME_LAMBDA
+            return true;
+        };
+#undef JAAD_BOUND_RETURN
+#define JAAD_BOUND_RETURN return
+        // A frame's window/OLA writes the new overlap into fresh registers while the old one is
+        // still an operand, so a loop of one body ends with 16 v_mov_b64 that copy the new set
+        // back.  With two bodies the sets swap roles and the back edge has no copy; an odd count
+        // leaves after the first body.  Everything per frame (handshake, prefetch, vmem_drain,
+        // skip-list step, emit) is as in the single body.
+        static_assert(kFast, "only the +-1 LSB modes are built with the unrolled frame loop");
+        for (int it = 0; it < my_n; it += 2) {
+            if (!frame(it)) return;
+            if (it + 1 >= my_n) break;
+            if (!frame(it + 1)) return;
         }
+#else
+        }
+#endif
         STAMP(11);
         // (done: no longer ahead of its mates)
         if constexpr (kFast) __hip_atomic_store(&S.rem[wave], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
