@@ -100,6 +100,23 @@ PARSE_EXPORTS = ["jaad_asc_parse", "jaad_adts_find", "jaad_adts_cfg", "jaad_raw_
                  "jaad_parser_pns_state", "jaad_parser_set_pns_state", "jaad_parse_frame", "jaad_probe_sbr"]
 
 
+# every symbol include/jaad_gparse.h declares (the device bitstream front end)
+GPARSE_EXPORTS = ["jaad_gparse_create", "jaad_gparse_destroy", "jaad_gparse_batch", "jaad_gparse_last_ms"]
+PNS_STATE0 = 0x1F2E3D4C  # the static ICStream.randomState of a fresh parser
+GPARSE_STATE_DTYPE = np.dtype([("pns_state", "<u4"), ("window_shape", "u1", (2,)), ("reserved", "u1", (2,))])
+assert GPARSE_STATE_DTYPE.itemsize == 8
+
+
+class GparseIn(C.Structure):
+    _fields_ = [("n_frames", C.c_uint32), ("n_runs", C.c_uint32), ("frame_begin", C.c_void_p), ("data", C.c_void_p),
+                ("data_bytes", C.c_size_t), ("frame_off", C.c_void_p), ("frame_len", C.c_void_p), ("state", C.c_void_p)]
+
+
+class GparseOut(C.Structure):
+    _fields_ = [("q", C.c_void_p), ("sf", C.c_void_p), ("cb", C.c_void_p), ("ics", C.c_void_p),
+                ("ms_used", C.c_void_p), ("tns", C.c_void_p)]
+
+
 class AdtsHeader(C.Structure):
     _fields_ = [("profile", C.c_uint8), ("sf_index", C.c_uint8), ("channel_config", C.c_uint8),
                 ("protection_absent", C.c_uint8), ("n_raw_blocks", C.c_uint8), ("reserved", C.c_uint8 * 3),
@@ -180,6 +197,11 @@ def load_lib(path) -> C.CDLL:
     L.jaad_parser_set_pns_state.restype = None
     L.jaad_parse_frame.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(FrameOut)]
     L.jaad_probe_sbr.argtypes = [C.POINTER(StreamCfg), C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32)]
+    L.jaad_gparse_create.argtypes = [C.POINTER(StreamCfg), C.c_int, C.POINTER(C.c_void_p)]
+    L.jaad_gparse_destroy.argtypes = [C.c_void_p]
+    L.jaad_gparse_destroy.restype = None
+    L.jaad_gparse_batch.argtypes = [C.c_void_p, C.POINTER(GparseIn), C.POINTER(GparseOut), C.c_void_p, C.c_void_p]
+    L.jaad_gparse_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     return L
 
 
@@ -744,3 +766,141 @@ class Parser:
             b.cce_ics = np.ascontiguousarray(np.array([r[3] for r in recs], ICS_DTYPE))
             b.cce_terms = np.ascontiguousarray(np.concatenate(terms)) if terms else np.zeros(0, CCE_TERM_DTYPE)
         return b
+
+
+# ---------------------------------------------------------------------------------------------
+# device bitstream front end (include/jaad_gparse.h)
+# ---------------------------------------------------------------------------------------------
+def gparse_state(n_runs: int, pns_state=PNS_STATE0) -> np.ndarray:
+    """jaad_gparse_state [n_runs] of fresh parsers (pns_state: one value or one per run)."""
+    st = np.zeros(n_runs, GPARSE_STATE_DTYPE)
+    st["pns_state"] = pns_state
+    return st
+
+
+@dataclass
+class DeviceRecords:
+    """What DeviceParser.parse_frames leaves on the device: the record tensors (torch, kept alive
+    here), their pointers as Context.decode_device takes them, and the Batch shell that goes with
+    them (runs, slots and the frame_status made of the frames that ended early)."""
+
+    tensors: dict
+    dev: dict
+    batch: Batch
+    frame_result: np.ndarray  # int8 [n_frames]: jaad_parse_frame's status per frame
+    state: np.ndarray         # GPARSE_STATE_DTYPE [n_runs] after the call
+    status: int = OK          # jaad_gparse_batch's return value
+
+
+class DeviceParser:
+    """Owns a jaad_gparse: AAC-LC raw_data_blocks in device memory -> batch records in device
+    memory (mono / stereo, no SBR).  There is no host fallback: without a gfx950 device the
+    constructor raises JaadError(ERR_NO_DEVICE)."""
+
+    def __init__(self, cfg: StreamCfg, device: int = 0):
+        self.cfg = cfg
+        self.nch = core_channels(cfg)
+        self.device = device
+        h = C.c_void_p()
+        rc = lib().jaad_gparse_create(C.byref(cfg), device, C.byref(h))
+        if rc:
+            raise JaadError(rc, "jaad_gparse_create")
+        self.h = h
+
+    def close(self):
+        h = getattr(self, "h", None)
+        if h:
+            self.h = None
+            lib().jaad_gparse_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except TypeError:  # interpreter shutdown (see Context.__del__)
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def parse(self, frame_begin: np.ndarray, data_ptr: int, data_bytes: int, frame_off_ptr: int, frame_len_ptr: int,
+              state: np.ndarray, out: dict, stream_ptr: int | None = None) -> tuple[int, np.ndarray]:
+        """jaad_gparse_batch over device pointers.  `out` maps q / sf / cb / ics (/ ms_used / tns) to
+        device pointers; `state` (GPARSE_STATE_DTYPE [n_runs]) advances in place when the call
+        returns 0.  Returns (status, frame_result int8 [n_frames])."""
+        fb = np.ascontiguousarray(frame_begin, np.uint32)
+        assert state.dtype == GPARSE_STATE_DTYPE and state.flags["C_CONTIGUOUS"] and len(state) == len(fb) - 1
+        nf = int(fb[-1]) if len(fb) else 0
+        res = np.zeros(max(nf, 1), np.int8)
+        gin = GparseIn(nf, len(fb) - 1, _ptr(fb), data_ptr, data_bytes, frame_off_ptr, frame_len_ptr, _ptr(state))
+        gout = GparseOut(out.get("q"), out.get("sf"), out.get("cb"), out.get("ics"), out.get("ms_used"), out.get("tns"))
+        rc = lib().jaad_gparse_batch(self.h, C.byref(gin), C.byref(gout), _ptr(res), stream_ptr)
+        return rc, res[:nf]
+
+    def last_ms(self) -> tuple[float, float, float]:
+        """Device milliseconds of the last parse: zeroing the rows, the frame kernel, the link kernel."""
+        ms = (C.c_float * 3)()
+        rc = lib().jaad_gparse_last_ms(self.h, ms)
+        if rc:
+            raise JaadError(rc, "jaad_gparse_last_ms")
+        return tuple(float(x) for x in ms)
+
+    def parse_frames(self, runs: list, state: np.ndarray | None = None, slots=None, with_tns: bool = True,
+                     check: bool = True) -> DeviceRecords:
+        """Runs of raw_data_blocks (a list of lists of bytes) -> records on the device.  The bytes go
+        up once through torch; the work is queued on torch's current stream, where a following
+        Context.decode_device(rec.dev, rec.batch, ..., stream_ptr=...) finds the records ready.
+        check: a frame status other than 0 / ERR_EOS raises JaadError (else see .status)."""
+        blob = b"".join(f for r in runs for f in r)
+        lens = np.array([len(f) for r in runs for f in r], np.uint32)
+        offs = np.zeros(len(lens), np.uint64)
+        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+        fb = np.zeros(len(runs) + 1, np.uint32)
+        fb[1:] = np.cumsum([len(r) for r in runs])
+        rec = self.parse_blob(np.frombuffer(blob, np.uint8) if blob else np.zeros(4, np.uint8), offs, lens, fb, state,
+                              slots, with_tns)
+        if check and rec.status:
+            raise JaadError(rec.status, "jaad_gparse_batch")
+        return rec
+
+    def parse_blob(self, data: np.ndarray, frame_off: np.ndarray, frame_len: np.ndarray, frame_begin: np.ndarray,
+                   state: np.ndarray | None = None, slots=None, with_tns: bool = True) -> DeviceRecords:
+        """One byte buffer (uint8, e.g. whole ADTS streams) with each frame's offset and length."""
+        import torch
+        dv = torch.device("cuda", self.device)
+        nf, nch, n_runs = len(frame_len), self.nch, len(frame_begin) - 1
+        ncf = nf * nch
+        up = lambda a, dt: torch.from_numpy(np.require(a, requirements=["C", "W"]).view(dt)).to(dv)
+        t = dict(data=up(data, np.uint8), frame_off=up(np.asarray(frame_off, np.uint64), np.int64),
+                 frame_len=up(np.asarray(frame_len, np.uint32), np.int32),
+                 q=torch.empty((ncf, 1024), dtype=torch.int16, device=dv),
+                 sf=torch.empty((ncf, 128), dtype=torch.uint8, device=dv),
+                 cb=torch.empty((ncf, 128), dtype=torch.uint8, device=dv),
+                 ics=torch.empty((ncf, 16), dtype=torch.uint8, device=dv))
+        if nch == 2:
+            t["ms_used"] = torch.empty((nf, 2), dtype=torch.int64, device=dv)
+        if with_tns:
+            t["tns"] = torch.empty((ncf, TNS_DTYPE.itemsize), dtype=torch.uint8, device=dv)
+        if state is None:
+            state = gparse_state(n_runs)
+        out = {k: t[k].data_ptr() for k in ("q", "sf", "cb", "ics", "ms_used", "tns") if k in t}
+        stream = torch.cuda.current_stream(dv).cuda_stream
+        rc, res = self.parse(frame_begin, t["data"].data_ptr(), int(np.asarray(data).nbytes), t["frame_off"].data_ptr(),
+                             t["frame_len"].data_ptr(), state, out, stream)
+        eos = res == ERR_EOS
+        slots = np.arange(n_runs, dtype=np.uint32) if slots is None else np.ascontiguousarray(slots, np.uint32)
+        shell = Batch(None, None, None, None, None, None, slots, np.ascontiguousarray(frame_begin, np.uint32), nch,
+                      frame_status=eos.astype(np.uint8) if eos.any() else None)
+        return DeviceRecords(t, out, shell, res, state, rc)
+
+    def records_to_host(self, rec: DeviceRecords) -> Batch:
+        """The records of a DeviceRecords as a host Batch (tests, inspection)."""
+        t = rec.tensors
+        h = lambda k, dt: np.ascontiguousarray(t[k].cpu().numpy()).view(dt)
+        b = rec.batch
+        return Batch(h("q", np.int16), h("sf", np.uint8), h("cb", np.uint8), h("ics", ICS_DTYPE).reshape(-1),
+                     h("ms_used", np.uint64) if "ms_used" in t else None,
+                     h("tns", TNS_DTYPE).reshape(-1) if "tns" in t else None, b.stream_slot, b.frame_begin, b.nch,
+                     frame_status=b.frame_status)
