@@ -10,7 +10,19 @@
  * the differential check against jaad_parse_frame (jaadec_amd/csrc/jaad_parse_core.h): the
  * records equal jaad_parse_frame's byte for byte, and so does each frame's status.
  *
- * AAC-LC with channel_config 1 or 2, no SBR.  Same library as jaad_gpu.h (libjaadgpu.so).
+ * AAC-LC with channel_config 1 or 2: jaad_gparse_create / jaad_gparse_batch.
+ *
+ * HE-AAC (SBR, and PS on a mono core) with channel_config 1 or 2: jaad_gparse_create_sbr /
+ * jaad_gparse_batch_sbr.  A frame's parse is split.  The device takes the channel element, as
+ * above, and stops at the first fill element after it that carries an SBR payload; the frame's
+ * bits from there to its end -- its tail: fill / data-stream elements, the SBR / PS payload, the
+ * END element -- are small and sequential along a stream, and the host parses them.  A scan and a
+ * gather kernel pack all tails, each shifted to bit 0 of an 8-byte aligned slot, into one pool that
+ * goes back to the host in one copy; there the host parser's own element loop (jaad_parse_frame's)
+ * walks each run's tails in order with the SBR / PS history of that run's jaad_parser, and fills
+ * the jaad_sbr_frame records jaad_decode_batch_device takes from host memory.
+ *
+ * Same library as jaad_gpu.h (libjaadgpu.so).
  */
 #ifndef JAAD_GPARSE_H
 #define JAAD_GPARSE_H
@@ -19,6 +31,7 @@
 #include <stdint.h>
 
 #include "jaad_gpu.h"
+#include "jaad_parse.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -82,6 +95,36 @@ int jaad_gparse_batch(jaad_gparse* gp, const jaad_gparse_in* in, const jaad_gpar
  * zeroing the q / tns rows, ms[1] the frame kernel, ms[2] the link kernel.  For measurements
  * (tools/bench_gparse.py); JAAD_ERR_INVALID_ARG before the first batch. */
 int jaad_gparse_last_ms(jaad_gparse* gp, float ms[3]);
+
+/* An SBR configuration: sbr = 1 (ps = 1 only with channel_config 1), channel_config 1 or 2, any
+ * ext_sf_index jaad_parser_create accepts.  JAAD_ERR_UNSUPPORTED for sbr = 0 (jaad_gparse_create)
+ * and configurations 3..7, decided before a device is looked for; otherwise as jaad_gparse_create.
+ * The object serves jaad_gparse_batch_sbr only, one made by jaad_gparse_create jaad_gparse_batch
+ * only: the other entry returns JAAD_ERR_INVALID_ARG before any launch. */
+int jaad_gparse_create_sbr(const jaad_stream_cfg* cfg, int device, jaad_gparse** out);
+
+/* Parse a batch of an SBR configuration.  in / out as for jaad_gparse_batch; in->state is ignored:
+ * the carried state is parsers[r] (host [n_runs], each created with the parser object's
+ * configuration), run r's host parser.  Its PNS LCG and window shapes go in, and after a
+ * successful call it is exactly where jaad_parse_frame over the run's frames would have left it
+ * (LCG, shapes, SBR / PS history), so host and device parsing can alternate on a stream, and
+ * jaad_parser_clone / jaad_parser_copy stay the rollback tools.
+ * sbr (host [n_frames], out) gets each frame's jaad_sbr_frame: zero for a frame whose core did not
+ * parse, JAAD_SBR_UPSAMPLE for one without a payload, a payload read whole before the bitstream
+ * ended kept (jaad_parse.h).  frame_result[f] is what jaad_parse_frame returns for the frame with
+ * this configuration and without coupling outputs.  The core records are in device memory, ordered
+ * on the stream, as for jaad_gparse_batch; the call returns once sbr and frame_result are written.
+ * Returns JAAD_OK when every frame is 0 or JAAD_ERR_EOS, the parsers advanced; otherwise the first
+ * other status in frame order, every parser as it was.  JAAD_ERR_INVALID_ARG also when the tails
+ * together reach 2^32 - 16 bytes (frames that overlap in data). */
+int jaad_gparse_batch_sbr(jaad_gparse* gp, const jaad_gparse_in* in, const jaad_gparse_out* out, jaad_parser* const* parsers,
+                          jaad_sbr_frame* sbr, int8_t* frame_result, void* hip_stream);
+
+/* Times of the last jaad_gparse_batch_sbr in milliseconds: ms[0] zeroing the q / tns rows, ms[1]
+ * the frame kernel, ms[2] the link kernel, ms[3] the scan and the gather kernel, ms[4] the copy of
+ * the pool to the host (HIP events on the call's stream), ms[5] the host tail stage (wall clock).
+ * JAAD_ERR_INVALID_ARG before the first such batch. */
+int jaad_gparse_last_ms_sbr(jaad_gparse* gp, float ms[6]);
 
 #ifdef __cplusplus
 }

@@ -34,12 +34,17 @@ def adts_index(data: bytes):
     return first, np.array(offs, np.uint64), np.array(lens, np.uint32)
 
 
-def decode_adts_streams(streams: list, flags: int = N.PCM_BIG_ENDIAN, pns_state=N.PNS_STATE0, device: int = 0) -> list:
+def decode_adts_streams(streams: list, flags: int = N.PCM_BIG_ENDIAN, pns_state=N.PNS_STATE0, device: int = 0,
+                        implicit_sbr: bool = False) -> list:
     """ADTS byte streams of one AAC-LC mono / stereo configuration -> PCM, one uint8 array
     [n_frames, frame_bytes] per stream.  The host only walks the ADTS headers; the bytes go up once,
     are parsed and decoded on the device, and the PCM comes back.  Frames whose bitstream ends early
     are dropped as the reference drops them (their PCM rows stay zero).  pns_state: the PNS LCG each
-    stream's parser starts from (one value or one per stream)."""
+    stream's parser starts from (one value or one per stream).
+    implicit_sbr: each stream's first frame is probed for an SBR payload (native.probe_sbr), and a
+    stream that has one is opened as the facade opens it (native.implicit_sbr_cfg: output rate
+    doubled, PS on a mono core): the device parses the core, the host the SBR / PS payloads
+    (native.SbrDeviceParser), and the PCM rows are 2048 samples per channel."""
     import torch
     if not streams:
         return []
@@ -49,6 +54,8 @@ def decode_adts_streams(streams: list, flags: int = N.PCM_BIG_ENDIAN, pns_state=
         if h is None:
             raise N.JaadError(N.ERR_EOS, "no ADTS frame found")
         c = N.adts_cfg(h)
+        if implicit_sbr and N.probe_sbr(c, bytes(s)[int(o[0]):int(o[0]) + int(n[0])]):
+            c = N.implicit_sbr_cfg(c)
         if cfg is None:
             cfg = c
         elif bytes(c) != bytes(cfg):
@@ -59,9 +66,15 @@ def decode_adts_streams(streams: list, flags: int = N.PCM_BIG_ENDIAN, pns_state=
         at += len(s)
     blob = np.frombuffer(b"".join(bytes(s) for s in streams), np.uint8)
     n_runs, nf = len(streams), fb[-1]
-    with N.DeviceParser(cfg, device) as gp, N.Context(cfg, n_runs, device) as ctx:
-        rec = gp.parse_blob(blob, np.concatenate(offs), np.concatenate(lens), np.array(fb, np.uint32),
-                            N.gparse_state(n_runs, pns_state))
+    with (N.SbrDeviceParser if cfg.sbr else N.DeviceParser)(cfg, device) as gp, N.Context(cfg, n_runs, device) as ctx:
+        if cfg.sbr:
+            parsers = [N.Parser(cfg) for _ in range(n_runs)]
+            for p, s0 in zip(parsers, np.broadcast_to(np.asarray(pns_state, np.uint32), (n_runs,))):
+                p.pns_state = int(s0)
+            state = parsers
+        else:
+            state = N.gparse_state(n_runs, pns_state)
+        rec = gp.parse_blob(blob, np.concatenate(offs), np.concatenate(lens), np.array(fb, np.uint32), state)
         if rec.status:
             bad = int(np.flatnonzero((rec.frame_result != 0) & (rec.frame_result != N.ERR_EOS))[0])
             raise N.JaadError(rec.status, f"jaad_gparse_batch (frame {bad})")

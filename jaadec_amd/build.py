@@ -48,7 +48,7 @@ def _deps(*globs: str) -> list[Path]:
 
 # sources of libjaadgpu.so (jaadec_amd/csrc): kernels, the C-ABI host code, the bitstream front end
 GPU_SRCS = ["jaad_lc.hip", "jaad_lc_fast.hip", "jaad_sbr.hip", "jaad_ps.hip", "jaad_gparse.hip", "jaad_capi.cpp",
-            "jaad_sbr_host.cpp", "jaad_parse.cpp", "jaad_parse_sbr.cpp", "jaad_mp4.cpp"]
+            "jaad_sbr_host.cpp", "jaad_parse.cpp", "jaad_parse_sbr.cpp", "jaad_parse_tail.cpp", "jaad_mp4.cpp"]
 # per-source extra flags (the LC kernel: see DESIGN.md §4a, scheduler strategy)
 GPU_FILE_FLAGS: dict[str, list[str]] = {
     # the +-1 LSB LC kernels (modes 4, 6): LLVM's iterative-ILP machine scheduler (-2.2 % on C2, round 6)

@@ -874,34 +874,36 @@ int cce_terms(const CceElem* cces, int n_cce, const ChElem* els, int n_el, jaad_
 // 14496-3 Table 1.19; configuration 4 ends with a back SCE)
 bool mc_lfe(const Cfg& C, int e) { return (C.cfg.channel_config == 6 || C.cfg.channel_config == 7) && e == C.n_elem - 1; }
 
-// One raw_data_block into `out`, moving the parse state ns / nsel (multichannel HE-AAC: SBR
-// state of elements 1..) as the reference moves its fields; parse_frame commits them.
-// probe != nullptr: stop at the first SBR extension payload after the channel element (bit 0 of
-// *probe).
-int parse_frame_body(const jaad_parser* p, const uint8_t* data, size_t bytes, jaad_frame_out* out, uint32_t* probe,
-                     ParseState& ns, std::vector<SbrParseState>& nsel)
-{
-    if (!p || !out || (!data && bytes) || !out->q || !out->sf || !out->cb || !out->ics) return JAAD_ERR_INVALID_ARG;
-    const Cfg& C = p->C;
-    int n_cpe = 0;
-    for (int k = 0; k < C.n_elem; k++) n_cpe += C.elem_nch[k] == 2;
-    if (n_cpe && !out->ms_used) return JAAD_ERR_INVALID_ARG;
-    if (C.cfg.sbr && !out->sbr) return JAAD_ERR_INVALID_ARG;
-    BitReader br(data, bytes);
+// Where the element loop of a frame stands: a whole frame starts from the defaults, the tail of a
+// frame whose channel element was parsed elsewhere (parse_tail_frame) after that element.
+struct ElemWalk {
     bool have_channels = false;
     int elem = 0, ch0 = 0, cpe = 0;  // channel elements parsed so far, their channels, CPEs
-    // SBR records: one per channel element (multichannel: out->sbr[0 .. n_elem), element order)
     uint32_t sbr_seen = 0;           // bit k: element k carried an SBR payload this frame
-    if (C.cfg.sbr) std::memset(out->sbr, 0, sizeof *out->sbr * (size_t)C.n_elem);
     ChElem els[8];
     int n_els = 0;
     std::vector<CceElem> cces;  // 7.7 KB each: only when the frame has CCEs
     int n_cce = 0;
-    out->n_cce = out->n_cce_terms = 0;
+    bool keep_sbr_on_refusal = true;  // false: the caller drops ns when the frame is refused
+};
+constexpr int kProbeHit = 1;  // element_loop: the probe found its SBR payload
+
+// The element loop of one raw_data_block up to its END element, into `out`, moving the parse state
+// ns / nsel (multichannel HE-AAC: SBR state of elements 1..) as the reference moves its fields.
+// probe != nullptr: stop at the first SBR extension payload after the channel element (bit 0 of
+// *probe, kProbeHit).
+int element_loop(const Cfg& C, BitReader& br, jaad_frame_out* out, uint32_t* probe, ParseState& ns,
+                 std::vector<SbrParseState>& nsel, ElemWalk& W)
+{
+    bool& have_channels = W.have_channels;
+    int &elem = W.elem, &ch0 = W.ch0, &cpe = W.cpe, &n_els = W.n_els, &n_cce = W.n_cce;
+    uint32_t& sbr_seen = W.sbr_seen;
+    ChElem* els = W.els;
+    std::vector<CceElem>& cces = W.cces;
     for (;;) {
         if (br.left() < 3) return JAAD_ERR_EOS;
         const int id = (int)br.read(3);
-        if (id == 7) break;  // END
+        if (id == 7) return JAAD_OK;  // END
         if (id == 6) {       // FIL (SyntacticElements.decodeFIL, :169-203)
             if (br.left() < 4) return JAAD_ERR_EOS;
             int count = (int)br.read(4);
@@ -920,7 +922,7 @@ int parse_frame_body(const jaad_parser* p, const uint8_t* data, size_t bytes, ja
                 // stream with cfg.sbr = 1 (and cfg.ps = 1 for a mono core, SCE.isStereo)
                 if (probe) {
                     *probe |= 1u;
-                    return JAAD_OK;
+                    return kProbeHit;
                 }
                 if (!C.cfg.sbr) return JAAD_ERR_UNSUPPORTED;
                 // SyntacticElements.decodeSBR: the payload belongs to the last audio element
@@ -929,8 +931,14 @@ int parse_frame_body(const jaad_parser* p, const uint8_t* data, size_t bytes, ja
                 const int e = elem - 1;
                 if (C.n_elem > 1 && mc_lfe(C, e)) return JAAD_ERR_UNSUPPORTED;
                 SbrParseState& S = e == 0 ? ns.sbr : nsel[(size_t)e - 1];
-                const SbrParseState before = S;
-                const int st = parse_sbr(sub, C, C.elem_nch[e], type == 14, S, out->sbr[e]);
+                int st;
+                if (W.keep_sbr_on_refusal) {
+                    const SbrParseState before = S;
+                    st = parse_sbr(sub, C, C.elem_nch[e], type == 14, S, out->sbr[e]);
+                    if (st == JAAD_ERR_EOS) S = before;
+                } else {
+                    st = parse_sbr(sub, C, C.elem_nch[e], type == 14, S, out->sbr[e]);
+                }
                 if (st == JAAD_ERR_EOS) {
                     // The bitstream ends inside the SBR payload.  The reference has read as much of
                     // it as was there when its EOSException comes (SBR.decode: readHeader with its
@@ -939,7 +947,6 @@ int parse_frame_body(const jaad_parser* p, const uint8_t* data, size_t bytes, ja
                     // instead of dropped, so the stream cannot go on out of step (the parser keeps
                     // its state).  A frame cut after its SBR payload is dropped with the payload's
                     // record, header included (jaad_decode_batch applies it).
-                    S = before;
                     return JAAD_ERR_UNSUPPORTED;
                 }
                 if (st) return st;
@@ -1027,11 +1034,17 @@ int parse_frame_body(const jaad_parser* p, const uint8_t* data, size_t bytes, ja
         ch0 += C.elem_nch[elem];
         elem++;
     }
-    if (!have_channels) return JAAD_ERR_BITSTREAM;  // a frame without audio: nothing to decode
-    if (elem != C.n_elem) return JAAD_ERR_UNSUPPORTED;  // a frame without all the configuration's elements
+}
+
+// what follows a frame's END element: the checks on the frame as a whole, the records of elements
+// without an SBR payload, the coupling terms
+int frame_end(const Cfg& C, jaad_frame_out* out, ParseState& ns, ElemWalk& W)
+{
+    if (!W.have_channels) return JAAD_ERR_BITSTREAM;  // a frame without audio: nothing to decode
+    if (W.elem != C.n_elem) return JAAD_ERR_UNSUPPORTED;  // a frame without all the configuration's elements
     if (C.cfg.sbr)
         for (int e = 0; e < C.n_elem; e++) {
-            if (sbr_seen & (1u << e)) continue;
+            if (W.sbr_seen & (1u << e)) continue;
             // an SCE of a multichannel stream without SBR data would drop to one output channel in
             // the reference (SCE.process accepts dataR only with SBR, A/syntax/SCE.java:122-132),
             // changing the frame's channel count: refused.  CPEs and LFEs are upsampled.
@@ -1039,12 +1052,32 @@ int parse_frame_body(const jaad_parser* p, const uint8_t* data, size_t bytes, ja
             const int st = sbr_missing(C, ns, out->sbr[e]);
             if (st) return st;
         }
-    if (n_cce) {
-        const int st = cce_terms(cces.data(), n_cce, els, n_els, out);
+    if (W.n_cce) {
+        const int st = cce_terms(W.cces.data(), W.n_cce, W.els, W.n_els, out);
         if (st) return st;
-        out->n_cce = (uint32_t)n_cce;
+        out->n_cce = (uint32_t)W.n_cce;
     }
     return JAAD_OK;
+}
+
+// One raw_data_block into `out`; parse_frame commits the state it moved.
+int parse_frame_body(const jaad_parser* p, const uint8_t* data, size_t bytes, jaad_frame_out* out, uint32_t* probe,
+                     ParseState& ns, std::vector<SbrParseState>& nsel)
+{
+    if (!p || !out || (!data && bytes) || !out->q || !out->sf || !out->cb || !out->ics) return JAAD_ERR_INVALID_ARG;
+    const Cfg& C = p->C;
+    int n_cpe = 0;
+    for (int k = 0; k < C.n_elem; k++) n_cpe += C.elem_nch[k] == 2;
+    if (n_cpe && !out->ms_used) return JAAD_ERR_INVALID_ARG;
+    if (C.cfg.sbr && !out->sbr) return JAAD_ERR_INVALID_ARG;
+    BitReader br(data, bytes);
+    // SBR records: one per channel element (multichannel: out->sbr[0 .. n_elem), element order)
+    if (C.cfg.sbr) std::memset(out->sbr, 0, sizeof *out->sbr * (size_t)C.n_elem);
+    out->n_cce = out->n_cce_terms = 0;
+    ElemWalk W;
+    const int st = element_loop(C, br, out, probe, ns, nsel, W);
+    if (st) return st == kProbeHit ? JAAD_OK : st;
+    return frame_end(C, out, ns, W);
 }
 
 // The state moves with a frame that parsed, and with one whose bitstream ended early as far as the
@@ -1064,6 +1097,61 @@ int parse_frame(jaad_parser* p, const uint8_t* data, size_t bytes, jaad_frame_ou
     return st;
 }
 }  // namespace
+
+// ---- the host half of a frame parsed in two places (jaad_parse_tail.h) -------------------------
+namespace jaad {
+namespace parse {
+
+const jaad_stream_cfg& parser_cfg(const jaad_parser* p) { return p->C.cfg; }
+
+void parser_core_state(const jaad_parser* p, uint32_t& pns, uint8_t shape[2])
+{
+    pns = p->st.pns;
+    shape[0] = (uint8_t)p->st.shape[0];
+    shape[1] = (uint8_t)p->st.shape[1];
+}
+
+void parser_set_core_state(jaad_parser* p, uint32_t pns, const uint8_t shape[2])
+{
+    p->st.pns = pns;
+    p->st.shape[0] = shape[0];
+    if (p->C.nch == 2) p->st.shape[1] = shape[1];
+}
+
+int parse_tail_frame(jaad_parser* p, int core_status, const uint8_t* tail, size_t phys_bytes, size_t bits, unsigned phase,
+                     jaad_sbr_frame* rec, bool in_place)
+{
+    const Cfg& C = p->C;
+    if (!C.cfg.sbr || C.n_elem != 1) return JAAD_ERR_INVALID_ARG;
+    std::memset(rec, 0, sizeof *rec);
+    if (core_status != JAAD_OK) return core_status;
+    auto walk = [&](ParseState& ns) {  // the element loop as after the channel element, then the frame's end
+        std::vector<SbrParseState> nsel;
+        jaad_frame_out o;
+        std::memset(&o, 0, sizeof o);  // no CCE outputs: a CCE in the tail is JAAD_ERR_UNSUPPORTED
+        o.sbr = rec;
+        ElemWalk W;
+        W.have_channels = true;
+        W.elem = 1;
+        W.ch0 = C.nch;
+        W.cpe = C.nch == 2;
+        W.keep_sbr_on_refusal = !in_place;
+        int st = JAAD_OK;
+        if (bits) {
+            BitReader br = BitReader::tail(tail, phys_bytes, bits, phase);
+            st = element_loop(C, br, &o, nullptr, ns, nsel, W);
+        }
+        return st ? st : frame_end(C, &o, ns, W);
+    };
+    if (in_place) return walk(p->st);  // p's own state moves, and is void when the frame is refused
+    ParseState ns = p->st;
+    const int st = walk(ns);
+    if (st == JAAD_OK || st == JAAD_ERR_EOS) p->st.sbr = ns.sbr;
+    return st;
+}
+
+}  // namespace parse
+}  // namespace jaad
 
 extern "C" {
 

@@ -7,6 +7,9 @@
 // its shape bit was read) and how many LCG steps its noise bands took.  A link pass (lcg_jump,
 // link_* below) turns those into jaad_ics_info.window_shape_prev / pns_state along a run.
 // tools/gparse_diff.cpp holds this file and jaad_parse.cpp together (tests/test_gparse_core.py).
+// For SBR configurations parse_frame_sbr stops where a frame's SBR payload begins and tail_dword
+// cuts what is left of the frame out for the host (tools/gparse_sbr_diff.cpp,
+// tests/test_gparse_sbr_core.py).
 //
 // No allocation, no exceptions, no statics; every loop is bounded by the bits left or a band
 // count.  Tables come in as one flat image of 32-bit words (jaad_gparse_image.h builds it).
@@ -504,9 +507,14 @@ JAAD_PC uint32_t bitrev32(uint32_t v)
 //   uint8_t* cb(int ch); uint8_t* sf(int ch); int16_t* q(int ch); jaad_tns* tns(int ch);
 //   void done(int ch);
 // F is valid for status 0 and, as far as shape_valid / noise_steps go, for JAAD_ERR_EOS.
-template <class B, class Out>
-JAAD_PC int parse_frame(B& br, const Cfg& C, Out& out, FrameInfo& F)
+// kSbr (an SBR configuration, parse_frame_sbr below): the first FIL element after the channel
+// element that holds an SBR payload (count != 0, its bytes are there, extension type 13 or 14) ends
+// the walk with JAAD_OK and tail_bit = the bit position of that FIL's id_syn_ele; what follows from
+// there on -- the frame's tail -- is the host's to parse.  tail_bit stays -1 otherwise.
+template <bool kSbr, class B, class Out>
+JAAD_PC int parse_frame_t(B& br, const Cfg& C, Out& out, FrameInfo& F, int64_t& tail_bit)
 {
+    tail_bit = -1;
     for (int c = 0; c < 2; c++) {
         F.ch[c].seq = F.ch[c].shape = F.ch[c].max_sfb = F.ch[c].grouping = F.ch[c].flags = F.ch[c].shape_valid = 0;
         F.ch[c].noise_steps = 0;
@@ -516,6 +524,7 @@ JAAD_PC int parse_frame(B& br, const Cfg& C, Out& out, FrameInfo& F)
     int elem = 0;
     for (;;) {
         if (br.left() < 3) return JAAD_ERR_EOS;
+        const int64_t at = br.pos;
         const int id = (int)br.read(3);
         if (id == 7) break;
         if (id == 6) {  // FIL
@@ -530,7 +539,11 @@ JAAD_PC int parse_frame(B& br, const Cfg& C, Out& out, FrameInfo& F)
             br.need(4);
             const int type = (int)br.peek(4);
             br.skip(8 * count);
-            if ((type == 13 || type == 14) && have_channels) return JAAD_ERR_UNSUPPORTED;  // SBR payload, core config
+            if ((type == 13 || type == 14) && have_channels) {
+                if (!kSbr) return JAAD_ERR_UNSUPPORTED;  // SBR payload, core config
+                tail_bit = at;
+                return JAAD_OK;
+            }
             continue;
         }
         if (br.left() < 4) return JAAD_ERR_EOS;
@@ -602,6 +615,38 @@ JAAD_PC int parse_frame(B& br, const Cfg& C, Out& out, FrameInfo& F)
     if (!have_channels) return JAAD_ERR_BITSTREAM;
     return JAAD_OK;
 }
+
+template <class B, class Out>
+JAAD_PC int parse_frame(B& br, const Cfg& C, Out& out, FrameInfo& F)
+{
+    int64_t tail_bit;
+    return parse_frame_t<false>(br, C, out, F, tail_bit);
+}
+template <class B, class Out>
+JAAD_PC int parse_frame_sbr(B& br, const Cfg& C, Out& out, FrameInfo& F, int64_t& tail_bit)
+{
+    return parse_frame_t<true>(br, C, out, F, tail_bit);
+}
+
+// ---- tail copy ---------------------------------------------------------------------------------
+// The bits [src_bit, src_bit + nbits) of a buffer, shifted to bit 0: dword k of the copy (the bits
+// 32k .. 32k + 31 of the tail, MSB first, as a big-endian value), zero from bit nbits on.
+// Src::dword_be(byte) returns the big-endian dword at an aligned byte offset and reads as zero,
+// without touching memory, past the buffer.
+template <class Src>
+JAAD_PC uint32_t tail_dword(const Src& src, uint64_t src_bit, uint64_t nbits, uint64_t k)
+{
+    if (32u * k >= nbits) return 0u;
+    const uint64_t p = src_bit + 32u * k;
+    const uint32_t at = (uint32_t)(p >> 5) * 4u, sh = (uint32_t)(p & 31u);
+    uint32_t w = src.dword_be(at) << sh;
+    const uint64_t rest = nbits - 32u * k;
+    if (sh && rest > 32u - sh) w |= src.dword_be(at + 4u) >> (32u - sh);
+    if (rest < 32u) w &= ~(0xFFFFFFFFu >> rest);
+    return w;
+}
+// bytes of a tail in the pool: whole bytes, rounded up to 8
+JAAD_PC uint32_t tail_pool_bytes(uint32_t bytes) { return (bytes + 7u) & ~7u; }
 
 // ---- link pass ---------------------------------------------------------------------------------
 // The LCG x -> 1664525 x + 1013904223 (mod 2^32) is affine, so n steps are one map (a, c).

@@ -14,9 +14,18 @@ namespace parse {
 // past the end return zero bits and set overrun(); callers check left() first where the
 // reference would throw EOSException.  sub() is readSubStream: a window of the next n bits
 // sharing the parent's absolute position (byte alignment stays absolute, as in the reference).
+// tail() reads bits that were cut out of a frame at bit `phase` (mod 8) and shifted to bit 0 of d:
+// byte alignment stays the frame's.
 class BitReader {
 public:
     BitReader(const uint8_t* d, size_t bytes) : d_(d), phys_(bytes), end_(bytes * 8), pos_(0) {}
+    static BitReader tail(const uint8_t* d, size_t phys_bytes, size_t bits, unsigned phase)
+    {
+        BitReader r(d, phys_bytes);
+        r.end_ = bits;
+        r.org_ = phase & 7u;
+        return r;
+    }
     int64_t left() const { return (int64_t)end_ - (int64_t)pos_; }
     bool overrun() const { return pos_ > end_; }
     size_t pos() const { return pos_; }
@@ -48,7 +57,7 @@ public:
         return v;
     }
     void skip(int64_t n) { pos_ += (size_t)(n > 0 ? n : 0); }
-    void byte_align() { pos_ = (pos_ + 7) & ~(size_t)7; }
+    void byte_align() { pos_ = ((pos_ + org_ + 7) & ~(size_t)7) - org_; }
     BitReader sub(int64_t n) const
     {
         BitReader r = *this;
@@ -114,6 +123,7 @@ private:
     const uint8_t* d_;
     size_t phys_;  // bytes of the caller's buffer (a sub-stream keeps its parent's)
     size_t end_, pos_;
+    size_t org_ = 0;  // the frame's bit phase of bit 0 (tail())
 };
 
 struct Cfg {

@@ -101,7 +101,8 @@ PARSE_EXPORTS = ["jaad_asc_parse", "jaad_adts_find", "jaad_adts_cfg", "jaad_raw_
 
 
 # every symbol include/jaad_gparse.h declares (the device bitstream front end)
-GPARSE_EXPORTS = ["jaad_gparse_create", "jaad_gparse_destroy", "jaad_gparse_batch", "jaad_gparse_last_ms"]
+GPARSE_EXPORTS = ["jaad_gparse_create", "jaad_gparse_destroy", "jaad_gparse_batch", "jaad_gparse_last_ms",
+                  "jaad_gparse_create_sbr", "jaad_gparse_batch_sbr", "jaad_gparse_last_ms_sbr"]
 PNS_STATE0 = 0x1F2E3D4C  # the static ICStream.randomState of a fresh parser
 GPARSE_STATE_DTYPE = np.dtype([("pns_state", "<u4"), ("window_shape", "u1", (2,)), ("reserved", "u1", (2,))])
 assert GPARSE_STATE_DTYPE.itemsize == 8
@@ -202,6 +203,10 @@ def load_lib(path) -> C.CDLL:
     L.jaad_gparse_destroy.restype = None
     L.jaad_gparse_batch.argtypes = [C.c_void_p, C.POINTER(GparseIn), C.POINTER(GparseOut), C.c_void_p, C.c_void_p]
     L.jaad_gparse_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.jaad_gparse_create_sbr.argtypes = [C.POINTER(StreamCfg), C.c_int, C.POINTER(C.c_void_p)]
+    L.jaad_gparse_batch_sbr.argtypes = [C.c_void_p, C.POINTER(GparseIn), C.POINTER(GparseOut), C.POINTER(C.c_void_p),
+                                        C.c_void_p, C.c_void_p, C.c_void_p]
+    L.jaad_gparse_last_ms_sbr.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     return L
 
 
@@ -788,8 +793,9 @@ class DeviceRecords:
     dev: dict
     batch: Batch
     frame_result: np.ndarray  # int8 [n_frames]: jaad_parse_frame's status per frame
-    state: np.ndarray         # GPARSE_STATE_DTYPE [n_runs] after the call
+    state: np.ndarray | None  # GPARSE_STATE_DTYPE [n_runs] after the call (DeviceParser)
     status: int = OK          # jaad_gparse_batch's return value
+    parsers: list | None = None  # SbrDeviceParser: the runs' host parsers, the carried state
 
 
 class DeviceParser:
@@ -904,3 +910,99 @@ class DeviceParser:
                      h("ms_used", np.uint64) if "ms_used" in t else None,
                      h("tns", TNS_DTYPE).reshape(-1) if "tns" in t else None, b.stream_slot, b.frame_begin, b.nch,
                      frame_status=b.frame_status)
+
+
+class SbrDeviceParser(DeviceParser):
+    """Owns a jaad_gparse made by jaad_gparse_create_sbr: HE-AAC raw_data_blocks (SBR, PS on a mono
+    core; mono / stereo) in device memory -> core records in device memory and the SBR records on
+    the host.  The carried state is one host Parser per run: the caller's, or parsers this object
+    creates and keeps (self.parsers) so that a stream goes on over several calls.  No host
+    fallback: without a gfx950 device the constructor raises JaadError(ERR_NO_DEVICE)."""
+
+    def __init__(self, cfg: StreamCfg, device: int = 0):
+        self.cfg = cfg
+        self.nch = core_channels(cfg)
+        self.device = device
+        self.parsers: list = []
+        h = C.c_void_p()
+        rc = lib().jaad_gparse_create_sbr(C.byref(cfg), device, C.byref(h))
+        if rc:
+            raise JaadError(rc, "jaad_gparse_create_sbr")
+        self.h = h
+
+    def close(self):
+        super().close()
+        for p in getattr(self, "parsers", []):
+            p.close()
+        self.parsers = []
+
+    def _parsers(self, n_runs: int, parsers) -> list:
+        if parsers is not None:
+            assert len(parsers) == n_runs
+            return list(parsers)
+        while len(self.parsers) < n_runs:
+            self.parsers.append(Parser(self.cfg))
+        return self.parsers[:n_runs]
+
+    def parse(self, frame_begin: np.ndarray, data_ptr: int, data_bytes: int, frame_off_ptr: int, frame_len_ptr: int,
+              parsers: list, out: dict, stream_ptr: int | None = None) -> tuple[int, np.ndarray, np.ndarray]:
+        """jaad_gparse_batch_sbr over device pointers; parsers: one Parser per run, advanced when the
+        call returns 0.  Returns (status, frame_result int8 [n_frames], SBR_FRAME_DTYPE [n_frames])."""
+        fb = np.ascontiguousarray(frame_begin, np.uint32)
+        assert len(parsers) == len(fb) - 1
+        nf = int(fb[-1]) if len(fb) else 0
+        res = np.zeros(max(nf, 1), np.int8)
+        sbr = np.zeros(max(nf, 1), SBR_FRAME_DTYPE)
+        hs = (C.c_void_p * max(len(parsers), 1))(*[p.h for p in parsers])
+        gin = GparseIn(nf, len(fb) - 1, _ptr(fb), data_ptr, data_bytes, frame_off_ptr, frame_len_ptr, None)
+        gout = GparseOut(out.get("q"), out.get("sf"), out.get("cb"), out.get("ics"), out.get("ms_used"), out.get("tns"))
+        rc = lib().jaad_gparse_batch_sbr(self.h, C.byref(gin), C.byref(gout), hs, _ptr(sbr), _ptr(res), stream_ptr)
+        return rc, res[:nf], sbr[:nf]
+
+    def last_ms(self) -> tuple[float, ...]:
+        """Milliseconds of the last parse: zeroing, frame kernel, link kernel, scan + gather, the
+        pool's copy to the host (device times), the host tail stage (wall clock)."""
+        ms = (C.c_float * 6)()
+        rc = lib().jaad_gparse_last_ms_sbr(self.h, ms)
+        if rc:
+            raise JaadError(rc, "jaad_gparse_last_ms_sbr")
+        return tuple(float(x) for x in ms)
+
+    def parse_frames(self, runs: list, parsers: list | None = None, slots=None, with_tns: bool = True,
+                     check: bool = True) -> DeviceRecords:
+        """As DeviceParser.parse_frames, with the runs' parsers in place of the state array."""
+        return super().parse_frames(runs, parsers, slots, with_tns, check)
+
+    def parse_blob(self, data: np.ndarray, frame_off: np.ndarray, frame_len: np.ndarray, frame_begin: np.ndarray,
+                   parsers: list | None = None, slots=None, with_tns: bool = True) -> DeviceRecords:
+        """One byte buffer with each frame's offset and length; rec.batch.sbr holds the SBR records."""
+        import torch
+        dv = torch.device("cuda", self.device)
+        nf, nch, n_runs = len(frame_len), self.nch, len(frame_begin) - 1
+        ncf = nf * nch
+        ps = self._parsers(n_runs, parsers)
+        up = lambda a, dt: torch.from_numpy(np.require(a, requirements=["C", "W"]).view(dt)).to(dv)
+        t = dict(data=up(data, np.uint8), frame_off=up(np.asarray(frame_off, np.uint64), np.int64),
+                 frame_len=up(np.asarray(frame_len, np.uint32), np.int32),
+                 q=torch.empty((ncf, 1024), dtype=torch.int16, device=dv),
+                 sf=torch.empty((ncf, 128), dtype=torch.uint8, device=dv),
+                 cb=torch.empty((ncf, 128), dtype=torch.uint8, device=dv),
+                 ics=torch.empty((ncf, 16), dtype=torch.uint8, device=dv))
+        if nch == 2:
+            t["ms_used"] = torch.empty((nf, 2), dtype=torch.int64, device=dv)
+        if with_tns:
+            t["tns"] = torch.empty((ncf, TNS_DTYPE.itemsize), dtype=torch.uint8, device=dv)
+        out = {k: t[k].data_ptr() for k in ("q", "sf", "cb", "ics", "ms_used", "tns") if k in t}
+        stream = torch.cuda.current_stream(dv).cuda_stream
+        rc, res, sbr = self.parse(frame_begin, t["data"].data_ptr(), int(np.asarray(data).nbytes), t["frame_off"].data_ptr(),
+                                  t["frame_len"].data_ptr(), ps, out, stream)
+        eos = res == ERR_EOS
+        slots = np.arange(n_runs, dtype=np.uint32) if slots is None else np.ascontiguousarray(slots, np.uint32)
+        shell = Batch(None, None, None, None, None, None, slots, np.ascontiguousarray(frame_begin, np.uint32), nch, sbr=sbr,
+                      frame_status=eos.astype(np.uint8) if eos.any() else None)
+        return DeviceRecords(t, out, shell, res, None, rc, ps)
+
+    def records_to_host(self, rec: DeviceRecords) -> Batch:
+        b = super().records_to_host(rec)
+        b.sbr = rec.batch.sbr
+        return b
